@@ -22,7 +22,14 @@ union over ranks is exactly the single-GPU match set (strong scaling: total
 work fixed).  The timed region is bracketed by barrier + synchronize and the
 max over ranks is reported.
 
-Parity (every run): rank 0 checks the TIMED step's gathered records, per
+A plain run (`--gpus N --steps K --warmup W`) sets up, settles the clock,
+runs the W warmup and the K timed steps and prints the result line; with
+`--dump-outputs DIR` it also writes the last timed step's records to
+DIR/*.npy (dump_outputs below).  Everything else is a side leg behind
+`--full`: the read-ceiling probe, parity, the CPU baseline and the two
+end-to-end lines (their fields are null in a plain run's line).
+
+Parity (`--full`): rank 0 checks the TIMED step's gathered records, per
 block, against the oracle (oracle/oracle.c, the scalar restatement) over all
 4 GiB, order-exact: the block's (end, id) sequence as sorted on the device
 equals the oracle's callback sequence element for element (`parity_bytes` =
@@ -30,7 +37,8 @@ bytes checked).  The end_to_end line's delivered (id, from, to) sequences are
 checked per block against oracle/hs_lit.py (digest + count).
 
 Extra JSON fields: roofline (rank 0's scan kernel from hipEvents vs the 8 TB/s
-MI355X peak; PMC traffic from profiles/), cpu_baseline (the SSE2 port of
+MI355X peak; PMC traffic from profiles/; with `--full` the measured read
+ceiling beside it), and with `--full` cpu_baseline (the SSE2 port of
 the reference FDR main loop over the same 4 GiB, one pinned thread per
 physical core the process may use, capped by the cgroup CPU quota, its match
 set checked too).
@@ -163,6 +171,13 @@ def main():
     ap.add_argument("--gib", type=float, default=4.0, help="corpus GiB (whole job)")
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--lits", type=int, default=5000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (what scan_wait / results hand "
+                         "a caller) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs around the timed steps: the read-ceiling "
+                         "probe, full-corpus parity against the oracle, the CPU baseline, the "
+                         "end-to-end and cfg-5-proxy lines (each has a --no-* switch below)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline timing")
     ap.add_argument("--no-e2e", action="store_true",
                     help="skip the end-to-end (matches delivered to the host) line")
@@ -345,7 +360,7 @@ def run(args):
     # (untimed; a plain 16-byte-load kernel, vsa_read_ceiling): the HBM rate
     # a scan could reach here, beside the 8 TB/s spec peak
     ceiling = None
-    if not args.no_ceiling:
+    if args.full and not args.no_ceiling:
         ceiling = ctx.read_ceiling(data.data_ptr(), data.numel(), 5)
     if dist is not None:
         dist.barrier()
@@ -380,17 +395,21 @@ def run(args):
     ms_step = el / args.steps * 1e3
     gbs = total / (el / args.steps) / 1e9
 
-    # records of the last timed step, global offsets (rank 0)
-    if rank == 0:
+    # records of the last timed step, global offsets (rank 0): read back
+    # only for the parity check and --dump-outputs
+    full = args.full
+    if rank == 0 and ((full and not args.no_parity) or args.dump_outputs):
         if dist is None:
             res = last.results(nm)
             keys, ids = res["key"], res["id"].astype(np.uint64)
         else:
             keys = st["keys"].cpu().numpy().view(np.uint64)
             ids = st["ids"].cpu().numpy().astype(np.uint64)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, keys, ids, counts)
     kavg = float(np.mean(kms))
     e2e = None
-    if world == 1 and not args.no_e2e:
+    if world == 1 and full and not args.no_e2e:
         try:
             e2e = end_to_end(lits, data.data_ptr(), bl, nblocks, total, nm, args.steps)
         except Exception as e:  # a side measurement never voids the bench line
@@ -398,7 +417,7 @@ def run(args):
     del data
     torch.cuda.empty_cache()
     cfg5 = None
-    if world == 1 and not args.no_cfg5:
+    if world == 1 and full and not args.no_cfg5:
         try:
             cfg5 = cfg5_proxy(torch, dev, args.steps, args.no_parity, args.cpu_threads)
         except Exception as e:  # a side measurement never voids the bench line
@@ -409,7 +428,8 @@ def run(args):
     # the CPU baseline is timed at N = 1 only (on rank 0); N > 1 runs check
     # parity alone
     with_cpu = not args.no_cpu and world == 1
-    if rank == 0:
+    parity, parity_bytes, cpu = None, 0, None
+    if rank == 0 and full:
         import oracle
         # one pinned thread per physical core the process may use
         # (all physical host cores), capped by the cgroup CPU
@@ -424,7 +444,6 @@ def run(args):
         threads = args.cpu_threads or cap
         oracle.set_pin(pins)
         eng = vsa.engine_blob(blob)
-        parity, parity_bytes, cpu = None, 0, None
         if not args.no_parity:
             # order-exact: the timed step's (end, id) sequence of every block,
             # in the order the device sort put it (end, bucket, LitInfo chain =
@@ -510,6 +529,7 @@ def run(args):
                                  "unpinned), its own domain-%d table, %d threads over "
                                  "contiguous stripes (7-byte halo); host: %s" % (parity_bytes, blob_domain(blob), threads,
                                                      _cpu_model())}
+    if rank == 0:
         alg_bytes = local_bytes + 16 * nm // world  # rank 0's input + its share of records
         achieved = alg_bytes / (kavg * 1e-3) / 1e9
         traffic = None
@@ -555,6 +575,7 @@ def run(args):
                          "scope": "rank 0 scan kernel (%d input bytes)" % local_bytes},
             "cpu_baseline": cpu,
             "pipeline": nslot,
+            "full": full,
             "end_to_end": e2e,
             "end_to_end_cfg5proxy": cfg5,
             "settle": {"launches": settle_n, "s": round(t_settle, 3),
@@ -570,6 +591,43 @@ def run(args):
     db.close()
     for c in ctxs:
         c.close()
+
+
+DUMP_CAP_BYTES = 48 << 20  # --dump-outputs: all files together stay well under 64 MB
+
+
+def dump_outputs(out_dir, keys, ids, counts):
+    """--dump-outputs: what the timed path handed its caller in the last
+    timed step, as float64 .npy files (every value is an integer below 2^53,
+    so float64 holds it exactly):
+      match_end.npy      end offset of every record in the corpus, in the
+                         order the device sort delivered them (key >> 24)
+      match_order.npy    the key's low 24 bits (the sort's tie-break within
+                         one end offset: bucket and LitInfo chain position)
+      match_id.npy       the record's literal id
+      step_counts.npy    the match count every timed step returned
+      sample_index.npy   the positions in the record sequence the three
+                         match_* files hold: all of them, or past the size
+                         cap a fixed seeded sample in ascending order
+    The inputs are seeded, so two builds run with the same arguments can be
+    compared file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(keys)
+    rows = DUMP_CAP_BYTES // (4 * 8)
+    if n > rows:
+        sel = np.sort(np.random.default_rng(20240607).choice(n, rows, replace=False))
+    else:
+        sel = np.arange(n)
+    k = np.asarray(keys, np.uint64)[sel]
+    arrays = {
+        "match_end": k >> np.uint64(24),
+        "match_order": k & np.uint64(0xFFFFFF),
+        "match_id": np.asarray(ids)[sel],
+        "step_counts": np.asarray(counts),
+        "sample_index": sel,
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
 
 
 def end_to_end(lits, d_data, bl, nblocks, total, hwlm_records, reps):

@@ -32,8 +32,8 @@ def test_gpu_bench_stripes_gloo(gpus):
     env["VSA_BENCH_BACKEND"] = "gloo"
     env["PYTHONUNBUFFERED"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus),
-           "--gib", "0.0625", "--blocks", "4", "--steps", "3", "--warmup", "1", "--no-cpu",
-           "--no-e2e"]
+           "--gib", "0.0625", "--blocks", "4", "--steps", "3", "--warmup", "1", "--full",
+           "--no-cpu", "--no-e2e"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -53,7 +53,7 @@ def test_gpu_bench_rccl_world1():
         env.pop(k, None)
     env["PYTHONUNBUFFERED"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist", "--gib", "0.0625",
-           "--blocks", "4", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-e2e"]
+           "--blocks", "4", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-e2e"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

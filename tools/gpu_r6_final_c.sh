@@ -5,9 +5,9 @@ set -e
 mkdir -p gpurun_out/final_c
 O=gpurun_out/final_c
 export HIP_FORCE_DEV_KERNARG=1 TMPDIR=/tmp
-timeout -k 10 500 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json
+timeout -k 10 500 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json
 python3 -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['cpu_baseline']['value'], d['end_to_end']['ms_per_pass'], d['end_to_end_cfg5proxy']['ms_per_gib'], d['parity'])"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o run -- python3 bench.py --no-cpu --no-e2e --no-cfg5 > $O/bench_trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o run -- python3 bench.py --full --no-cpu --no-e2e --no-cfg5 > $O/bench_trace.log 2>&1
 tail -1 $O/bench_trace.log | cut -c1-200
 B="python3 bench.py --steps 3 --warmup 2 --no-cpu --no-parity --no-e2e --no-cfg5 --no-ceiling"
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -f csv -d $O/fetch -o run -- $B > $O/bench_fetch.log 2>&1

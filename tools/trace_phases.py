@@ -3,7 +3,7 @@
     python tools/trace_phases.py TAG  ->  profiles/TAG_prof/lit_scan_phases.json
 
 Reads gpurun_out/prof_TAG/trace/*kernel_trace.csv (tools/profile.sh: the
-default `python3 bench.py` under rocprofv3 --kernel-trace) and the bench line
+full `python3 bench.py --full` under rocprofv3 --kernel-trace) and the bench line
 in bench_trace.log for the settle / warmup / steps counts.  Launches in
 dispatch order: settle (clock ramp), warmup, the timed steps, then the
 parity / end-to-end / other launches."""
@@ -29,7 +29,7 @@ assert bench is not None, "no bench line in bench_trace.log"
 ns, nw, nt = bench["settle"]["launches"], bench["warmup"], bench["steps"]
 cuts = [("settle (clock ramp)", 0, ns), ("warmup", ns, ns + nw),
         ("timed steps", ns + nw, ns + nw + nt), ("parity / end-to-end / other", ns + nw + nt, len(dur))]
-out = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py (tools/profile.sh %s); "
+out = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full (tools/profile.sh %s); "
                  "launches in dispatch order" % tag,
        "bench_kernel_ms_hip_events": bench["roofline"]["kernel_ms"], "phases": {}}
 for name, a, b in cuts:
