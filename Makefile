@@ -20,7 +20,7 @@ $(CSRC)/flood.o: $(CSRC)/flood.cpp $(CSRC)/hs_layout.h $(CSRC)/vsa_internal.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/hs_lit.o: $(CSRC)/hs_lit.cpp $(CSRC)/hs_layout.h $(CSRC)/vsa_internal.h \
-                  include/vectorscan_amd.h include/vectorscan_amd_hs.h
+                  $(CSRC)/hs_report.h include/vectorscan_amd.h include/vectorscan_amd_hs.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/kernels.o: $(CSRC)/kernels.hip $(CSRC)/kernels.h

@@ -169,6 +169,30 @@ static inline uint64_t vsa_hs_seq_digest_step(uint64_t h, unsigned id, unsigned 
 }
 int vsa_hs_corpus_free(vsa_hs_corpus_t *corpus);
 
+/* One final match of a block-mode corpus: `from` / `to` relative to its
+ * block. */
+typedef struct {
+    uint32_t id, block;
+    uint64_t from, to;
+} vsa_hs_match_t;
+/* The report program of a block-mode database -- long-literal check,
+ * exhaustion, dedupe, SOM log -- over caller-supplied HWLM records sorted by
+ * key (key = end << 24 | order, end relative to h_data; ids = HWLM literal
+ * ids), on the CPU, all buffers on the host; needs no GPU.  Each block
+ * (offsets / lens relative to h_data, as vsa_hs_corpus_prepare takes them)
+ * is one hs_scan: counts / digests (optional, nblocks each) as
+ * vsa_hs_corpus_scan_ex delivers them, out (optional, cap entries) the
+ * matches, blocks in index order, each block's in delivery order; at most
+ * cap are written, *total = all blocks' matches.  It walks the records one
+ * end-group at a time with no state but the exhaustion keys
+ * (vectorscan_amd/csrc/hs_report.h).
+ * A stream or vectored database returns VSA_HS_DB_MODE_ERROR. */
+int vsa_hs_report_records_host(const vsa_hs_database_t *db, const uint64_t *keys,
+                               const uint32_t *ids, uint64_t n, const uint8_t *h_data,
+                               const uint64_t *offsets, const uint64_t *lens, uint32_t nblocks,
+                               uint64_t *counts, uint64_t *digests, vsa_hs_match_t *out,
+                               uint64_t cap, uint64_t *total);
+
 /* Streams, continued: hs_copy_stream / hs_reset_and_copy_stream
  * (hs_runtime.h:291 / :324, runtime.c:713-779) and hs_stream_size
  * (hs_common.h:183). */

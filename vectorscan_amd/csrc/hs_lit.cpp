@@ -50,18 +50,19 @@
 #include "vectorscan_amd.h"
 #include "vectorscan_amd_hs.h"
 #include "vsa_internal.h"
+#include "hs_report.h"
 
 namespace {
 
 constexpr uint32_t DB_MAGIC = 0x56534c44u;      /* "VSLD" */
 constexpr uint32_t SCRATCH_MAGIC = 0x56534c53u; /* "VSLS" */
 constexpr uint32_t STREAM_MAGIC = 0x5653534du;  /* "VSSM" */
-constexpr size_t SHORT_LIT = 8;                 /* ROSE_SHORT_LITERAL_LEN_MAX */
+constexpr size_t SHORT_LIT = vsa_report::SHORT_LEN; /* ROSE_SHORT_LITERAL_LEN_MAX */
 constexpr size_t HIST_MIN = 16;                 /* history handed to the GPU */
 constexpr size_t LIMIT_PATTERN_LENGTH = 16000;  /* grey.cpp:148 */
 constexpr unsigned LIMIT_PATTERN_COUNT = 8000000; /* grey.cpp:147 */
-constexpr uint32_t NO_EKEY = ~0u;
-constexpr int KEY_END_SHIFT = 24; /* vsa_match_t.key: end << 24 */
+constexpr uint32_t NO_EKEY = vsa_report::NO_EKEY;
+constexpr int KEY_END_SHIFT = vsa_report::END_SHIFT; /* vsa_match_t.key: end << 24 */
 
 std::atomic<uint64_t> g_serial{1};
 
@@ -1353,6 +1354,117 @@ int vsa_hs_scan_corpus(const vsa_hs_database_t *db, vsa_hs_scratch_t *scratch,
     rc = vsa_hs_corpus_scan(c, counts, total, threads);
     vsa_hs_corpus_free(c);
     return rc;
+}
+
+/* ----------------------------------------- the report program, stateless --
+ * hs_report.h restates the report program per end-group, with exhaustion
+ * as the only state carried between groups.  vsa_hs_report_records_host runs it on the CPU
+ * over caller-supplied records; the host replay above is untouched. */
+namespace {
+
+/* a database flattened for hs_report.h: fragments in HWLM literal id order,
+ * each one's patterns in compile order, the prefixes of the long ones in one
+ * pool */
+struct ReportTables {
+    std::vector<uint32_t> frag_off;
+    std::vector<vsa_report::Pat> pats;
+    std::vector<uint8_t> pool;
+    vsa_report::Tables t{};
+};
+
+void build_report_tables(const vsa_hs_database *db, ReportTables &r) {
+    r.frag_off.push_back(0);
+    for (const auto &fr : db->frags) {
+        for (uint32_t pi : fr) {
+            const Pattern &p = db->pats[pi];
+            vsa_report::Pat q{};
+            q.id = p.id;
+            q.ekey = p.ekey;
+            q.len = (uint32_t)p.s.size();
+            q.flags = (p.caseless ? vsa_report::PAT_CASELESS : 0u) |
+                      (p.som ? vsa_report::PAT_SOM : 0u) |
+                      (p.som_dedupe ? vsa_report::PAT_SOM_DEDUPE : 0u);
+            q.pre = (uint32_t)r.pool.size();
+            if (p.s.size() > SHORT_LIT)
+                r.pool.insert(r.pool.end(), p.s.begin(), p.s.end() - SHORT_LIT);
+            r.pats.push_back(q);
+        }
+        r.frag_off.push_back((uint32_t)r.pats.size());
+    }
+    r.pool.push_back(0);
+    r.t.frag_off = r.frag_off.data();
+    r.t.pats = r.pats.data();
+    r.t.pool = r.pool.data();
+    r.t.n_frags = (uint32_t)db->frags.size();
+    r.t.n_pats = (uint32_t)r.pats.size();
+    r.t.n_ekeys = db->n_ekeys;
+    r.t.dedupe = db->dedupe;
+}
+
+struct HostEx {
+    std::vector<uint8_t> bits;
+    std::vector<uint32_t> touched;
+    bool test(uint32_t e) const { return bits[e]; }
+    void set(uint32_t e) {
+        bits[e] = 1;
+        touched.push_back(e);
+    }
+};
+
+struct HostEmit {
+    vsa_hs_match_t *out;
+    uint64_t cap, slot;
+    uint32_t block;
+    uint64_t cnt, h;
+    void operator()(uint32_t id, uint64_t from, uint64_t to) {
+        if (out && slot < cap) out[slot] = vsa_hs_match_t{id, block, from, to};
+        slot++;
+        cnt++;
+        h = vsa_hs_seq_digest_step(h, id, from, to);
+    }
+};
+
+} // namespace
+
+int vsa_hs_report_records_host(const vsa_hs_database_t *db, const uint64_t *keys,
+                               const uint32_t *ids, uint64_t n, const uint8_t *h_data,
+                               const uint64_t *offsets, const uint64_t *lens, uint32_t nblocks,
+                               uint64_t *counts, uint64_t *digests, vsa_hs_match_t *out,
+                               uint64_t cap, uint64_t *total) {
+    if (!valid_db(db) || !total || (n && (!keys || !ids)) || (nblocks && (!offsets || !lens)))
+        return VSA_HS_INVALID;
+    if (db->mode != VSA_HS_MODE_BLOCK) return VSA_HS_DB_MODE_ERROR;
+    if (db->max_len > SHORT_LIT && !h_data && nblocks) return VSA_HS_INVALID;
+    for (uint64_t k = 0; k < n; k++)
+        if (ids[k] >= db->frags.size() || (k && keys[k] < keys[k - 1])) return VSA_HS_INVALID;
+    ReportTables r;
+    build_report_tables(db, r);
+    HostEx ex;
+    ex.bits.assign(db->n_ekeys, 0);
+    HostEmit em{out, out ? cap : 0, 0, 0, 0, 0};
+    *total = 0;
+    for (uint32_t b = 0; b < nblocks; b++) {
+        const uint64_t off = offsets[b];
+        const uint64_t r0 = vsa_report::lower_bound_key(keys, n, off << KEY_END_SHIFT);
+        const uint64_t r1 = vsa_report::lower_bound_key(keys, n, (off + lens[b]) << KEY_END_SHIFT);
+        em.block = b;
+        em.cnt = em.h = 0;
+        for (uint64_t k = r0; k < r1;) {
+            const uint64_t end = keys[k] >> KEY_END_SHIFT;
+            uint64_t k1 = k + 1;
+            while (k1 < r1 && (keys[k1] >> KEY_END_SHIFT) == end) k1++;
+            vsa_report::report_group(r.t, ids, k, k1, h_data ? h_data + off : nullptr,
+                                     end - off + 1, ex, em);
+            k = k1;
+        }
+        /* every block is a fresh hs_scan */
+        for (uint32_t e : ex.touched) ex.bits[e] = 0;
+        ex.touched.clear();
+        if (counts) counts[b] = em.cnt;
+        if (digests) digests[b] = em.h;
+        *total += em.cnt;
+    }
+    return VSA_HS_SUCCESS;
 }
 
 /* runtime.c:545-575 */

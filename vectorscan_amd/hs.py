@@ -419,6 +419,43 @@ _sig("vsa_hs_corpus_scan_ex", ctypes.c_int, _vp, _vp, _vp, _u64p, ctypes.c_uint)
 _sig("vsa_hs_corpus_scan_repeats", ctypes.c_int, _vp, ctypes.c_uint32, _vp, _vp, _vp,
      ctypes.c_uint)
 _sig("vsa_hs_corpus_free", ctypes.c_int, _vp)
+_sig("vsa_hs_report_records_host", ctypes.c_int, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+     ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64, _u64p)
+
+# vsa_hs_match_t
+MATCH_DTYPE = np.dtype([("id", np.uint32), ("block", np.uint32), ("from", np.uint64),
+                        ("to", np.uint64)])
+
+
+def report_records_host(db, keys, ids, data, offsets, lens, cap=None):
+    """vsa_hs_report_records_host: the report program on the CPU over sorted
+    HWLM records (keys = end << 24 | order, ends relative to `data`), each
+    block one hs_scan.  Returns (rc, total, counts, digests, matches as a
+    MATCH_DTYPE array of at most cap entries; default: all)."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    ids = np.ascontiguousarray(ids, np.uint32)
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    ln = np.ascontiguousarray(lens, np.uint64)
+    hk, hp = None, None
+    if data is not None:
+        hk, hp, _ = _as_buf(data)
+    n = len(offs)
+    cnt, dg = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    total = ctypes.c_uint64()
+
+    def call(out, c):
+        return lib.vsa_hs_report_records_host(
+            db.handle, keys.ctypes.data, ids.ctypes.data, len(keys), hp, offs.ctypes.data,
+            ln.ctypes.data, n, cnt.ctypes.data, dg.ctypes.data,
+            out.ctypes.data if out is not None else None, c, ctypes.byref(total))
+    if cap is None:
+        rc = call(None, 0)
+        if rc:
+            return rc, 0, cnt, dg, np.zeros(0, MATCH_DTYPE)
+        cap = total.value
+    out = np.zeros(max(1, cap), MATCH_DTYPE)
+    rc = call(out, cap)
+    return rc, total.value, cnt, dg, out[:min(cap, total.value)]
 
 _M64 = (1 << 64) - 1
 
