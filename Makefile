@@ -19,8 +19,15 @@ $(CSRC)/compile.o: $(CSRC)/compile.cpp $(CSRC)/hs_layout.h $(CSRC)/vsa_internal.
 $(CSRC)/flood.o: $(CSRC)/flood.cpp $(CSRC)/hs_layout.h $(CSRC)/vsa_internal.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+REPORT_HDRS := $(CSRC)/hs_report.h $(CSRC)/hs_report_passes.h $(CSRC)/hs_report_device.h
+
 $(CSRC)/hs_lit.o: $(CSRC)/hs_lit.cpp $(CSRC)/hs_layout.h $(CSRC)/vsa_internal.h \
-                  $(CSRC)/hs_report.h include/vectorscan_amd.h include/vectorscan_amd_hs.h
+                  $(REPORT_HDRS) include/vectorscan_amd.h include/vectorscan_amd_hs.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the report program's passes on the device (hs_report_passes.h)
+$(CSRC)/report.o: $(CSRC)/report.hip $(REPORT_HDRS) $(CSRC)/vsa_internal.h $(CSRC)/hs_layout.h \
+                  include/vectorscan_amd.h include/vectorscan_amd_hs.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/kernels.o: $(CSRC)/kernels.hip $(CSRC)/kernels.h
@@ -44,7 +51,10 @@ $(CSRC)/batcher.o: $(CSRC)/batcher.hip $(RT_DEPS)
 
 RT_OBJS := $(CSRC)/runtime.o $(CSRC)/plan.o $(CSRC)/dropin.o $(CSRC)/batcher.o
 
-$(LIB): $(CSRC)/compile.o $(CSRC)/flood.o $(CSRC)/hs_lit.o $(CSRC)/kernels.o $(RT_OBJS)
+LIB_OBJS := $(CSRC)/compile.o $(CSRC)/flood.o $(CSRC)/hs_lit.o $(CSRC)/kernels.o $(RT_OBJS) \
+            $(CSRC)/report.o
+
+$(LIB): $(LIB_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@
 
 $(ORACLE): oracle/oracle.c
@@ -71,7 +81,33 @@ $(DROPIN): tools/dropin_threads.c include/vectorscan_amd.h $(LIB) $(ORACLE)
 	    -Loracle/_build -loracle -pthread -Wl,-rpath,'$$ORIGIN/../vectorscan_amd' \
 	    -Wl,-rpath,'$$ORIGIN/../oracle/_build'
 
-clean:
-	rm -f $(CSRC)/*.o $(LIB) $(ORACLE) $(HARNESS) $(HSNAMES) $(DROPIN)
+# CPU-only check of the report passes (tests/c/report_emul.cpp): the
+# emulated passes against the host walk, small shapes and 4 x 256 MiB of
+# offsets, with AddressSanitizer and UBSan on the host code of the
+# translation units that hold the passes; the rest linked as built.  Needs no
+# GPU.  Not part of `all`.
+SAN := -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer -g
+EMUL := tests/c/report_emul_asan
 
-.PHONY: all clean
+$(CSRC)/hs_lit.asan.o: $(CSRC)/hs_lit.cpp $(CSRC)/hs_layout.h $(CSRC)/vsa_internal.h \
+                       $(REPORT_HDRS) include/vectorscan_amd.h include/vectorscan_amd_hs.h
+	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -c $< -o $@
+
+$(CSRC)/report.asan.o: $(CSRC)/report.hip $(REPORT_HDRS) $(CSRC)/vsa_internal.h \
+                       $(CSRC)/hs_layout.h include/vectorscan_amd.h include/vectorscan_amd_hs.h
+	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -c $< -o $@
+
+tests/c/report_emul.asan.o: tests/c/report_emul.cpp include/vectorscan_amd_hs.h
+	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -c $< -o $@
+
+$(EMUL): tests/c/report_emul.asan.o $(CSRC)/hs_lit.asan.o $(CSRC)/report.asan.o \
+         $(filter-out $(CSRC)/hs_lit.o $(CSRC)/report.o,$(LIB_OBJS))
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $^ -o $@
+
+report-emul-asan: $(EMUL)
+	./$(EMUL)
+
+clean:
+	rm -f $(CSRC)/*.o tests/c/*.o $(LIB) $(ORACLE) $(HARNESS) $(HSNAMES) $(DROPIN) $(EMUL)
+
+.PHONY: all clean report-emul-asan

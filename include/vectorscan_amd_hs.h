@@ -12,8 +12,11 @@
  * order: increasing `to`; at one `to`, literal fragments in HWLM confirm
  * order, then patterns in compile order.
  *
- * Host buffers are copied to the GPU on every call; for device-resident
- * corpora use vsa_scan_blocks* directly.
+ * Host buffers are copied to the GPU on every call.  Device-resident corpora
+ * go through vsa_hs_corpus_prepare (report program on the host, from the
+ * scan's records) or vsa_hs_corpus_prepare_device (report program on the
+ * device: block mode, no host copy, the matches returned in HBM or copied
+ * out); vsa_scan_blocks* gives the raw HWLM records.
  */
 #ifndef VECTORSCAN_AMD_HS_H
 #define VECTORSCAN_AMD_HS_H
@@ -192,6 +195,50 @@ int vsa_hs_report_records_host(const vsa_hs_database_t *db, const uint64_t *keys
                                const uint64_t *offsets, const uint64_t *lens, uint32_t nblocks,
                                uint64_t *counts, uint64_t *digests, vsa_hs_match_t *out,
                                uint64_t cap, uint64_t *total);
+/* The same call computed the way the device computes it: the data-parallel
+ * passes of vectorscan_amd/csrc/hs_report_passes.h (lead, exhaustion by a
+ * stable sort of the keyed candidates, count, exclusive sums, emit) run in
+ * serial loops on the CPU, with the device path's buffer sizing and block
+ * table.  Same arguments and results as vsa_hs_report_records_host, except
+ * that non-empty blocks that overlap are refused (VSA_HS_INVALID), as
+ * vsa_hs_corpus_prepare_device refuses them.  Needs no GPU. */
+int vsa_hs_report_records_emulated(const vsa_hs_database_t *db, const uint64_t *keys,
+                                   const uint32_t *ids, uint64_t n, const uint8_t *h_data,
+                                   const uint64_t *offsets, const uint64_t *lens,
+                                   uint32_t nblocks, uint64_t *counts, uint64_t *digests,
+                                   vsa_hs_match_t *out, uint64_t cap, uint64_t *total);
+
+/* A block-mode corpus that lives only in HBM: the report program runs on the
+ * device (vectorscan_amd/csrc/report.hip), so no host copy of the corpus is
+ * needed or taken, whatever the literal lengths, and the matches themselves
+ * are returned.  Block-mode database only (else VSA_HS_DB_MODE_ERROR).
+ * Non-empty blocks must not overlap (VSA_HS_INVALID); zero-length blocks may
+ * lie anywhere.  Offsets and ends lie below 2^40.  Other errors and the
+ * VSA_MAX_BLOCKS limit as vsa_hs_corpus_prepare.  On such a corpus
+ * vsa_hs_corpus_scan / _scan_ex / _scan_repeats return VSA_HS_INVALID when
+ * the database has a literal longer than 8 bytes (their host replay would
+ * need the host copy) and work as usual otherwise. */
+int vsa_hs_corpus_prepare_device(const vsa_hs_database_t *db, vsa_hs_scratch_t *scratch,
+                                 const uint8_t *d_data, const uint64_t *offsets,
+                                 const uint64_t *lens, uint32_t nblocks,
+                                 vsa_hs_corpus_t **corpus);
+/* Scan plus report program on the device.  counts (optional, host, nblocks)
+ * and *total as vsa_hs_corpus_scan_ex delivers them; the matches stay on the
+ * device.  The scan is completed (output-overflow rescans, the fallback
+ * sort) before its records are read; the call returns when the matches are
+ * written. */
+int vsa_hs_corpus_scan_device(vsa_hs_corpus_t *corpus, uint64_t *counts, uint64_t *total);
+/* The last vsa_hs_corpus_scan_device's (or _scan_matches') matches: device
+ * pointer, valid until the next scan of the corpus or its free; blocks in
+ * index order, each block's matches in delivery order. */
+int vsa_hs_corpus_matches_device(vsa_hs_corpus_t *corpus, const vsa_hs_match_t **d_matches,
+                                 uint64_t *n);
+/* vsa_hs_corpus_scan_device plus a copy of the first min(cap, *total)
+ * matches to out (optional, cap entries).  counts / digests optional;
+ * digests are folded on the host from the copied matches and are therefore
+ * only available when cap >= *total (else VSA_HS_INVALID). */
+int vsa_hs_corpus_scan_matches(vsa_hs_corpus_t *corpus, vsa_hs_match_t *out, uint64_t cap,
+                               uint64_t *counts, uint64_t *digests, uint64_t *total);
 
 /* Streams, continued: hs_copy_stream / hs_reset_and_copy_stream
  * (hs_runtime.h:291 / :324, runtime.c:713-779) and hs_stream_size

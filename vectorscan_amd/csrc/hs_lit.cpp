@@ -42,6 +42,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <unistd.h>
@@ -50,7 +51,7 @@
 #include "vectorscan_amd.h"
 #include "vectorscan_amd_hs.h"
 #include "vsa_internal.h"
-#include "hs_report.h"
+#include "hs_report_device.h"
 
 namespace {
 
@@ -107,6 +108,9 @@ struct vsa_hs_scratch {
     std::atomic<bool> in_use{false};
     vsa_ctx_t *ctx = nullptr;
     std::vector<std::pair<uint64_t, vsa_db_t *>> dbs; /* serial -> device copy */
+    /* serial -> the database's report tables on the device, made by the
+     * first vsa_hs_corpus_prepare_device of that database */
+    std::vector<std::pair<uint64_t, vsa_report::DeviceTables *>> rtabs;
 };
 
 /* per-stream state: stream offset, the last bytes written (history), the
@@ -595,6 +599,7 @@ int vsa_hs_free_scratch(vsa_hs_scratch_t *scratch) {
     if (scratch->magic != SCRATCH_MAGIC) return VSA_HS_INVALID;
     if (scratch->in_use.exchange(true)) return VSA_HS_SCRATCH_IN_USE;
     for (auto &e : scratch->dbs) vsa_db_free(e.second);
+    for (auto &e : scratch->rtabs) vsa_report::device_tables_free(e.second);
     if (scratch->ctx) vsa_ctx_destroy(scratch->ctx);
     scratch->magic = 0;
     delete scratch;
@@ -700,19 +705,22 @@ struct vsa_hs_corpus {
     std::vector<uint64_t> p_off, p_len, p_hist;
     vsa_ctx_t *ctx2 = nullptr;
     vsa_plan_t *plan2 = nullptr;
+    /* vsa_hs_corpus_prepare_device: no host copy, the report program on the
+     * device */
+    vsa_report::DeviceReport *report = nullptr;
 };
 
-int vsa_hs_corpus_prepare(const vsa_hs_database_t *db, vsa_hs_scratch_t *scratch,
+static int corpus_prepare(const vsa_hs_database_t *db, vsa_hs_scratch_t *scratch,
                           const uint8_t *d_data, const uint8_t *h_data,
                           const uint64_t *offsets, const uint64_t *lens,
-                          const uint32_t *stream_ids, uint32_t nblocks,
+                          const uint32_t *stream_ids, uint32_t nblocks, bool device_report,
                           vsa_hs_corpus_t **out) {
     if (!valid_db(db) || !offsets || !lens || !out || (nblocks && !d_data))
         return VSA_HS_INVALID;
     /* one launch plan per corpus: at most VSA_MAX_BLOCKS chunks (the
      * reference has no such limit; a larger corpus is prepared in parts) */
     if (nblocks > VSA_MAX_BLOCKS) return VSA_HS_INVALID;
-    if (db->max_len > SHORT_LIT && !h_data) return VSA_HS_INVALID;
+    if (db->max_len > SHORT_LIT && !h_data && !device_report) return VSA_HS_INVALID;
     if (!scratch || scratch->magic != SCRATCH_MAGIC || !device_db(scratch, db))
         return VSA_HS_INVALID;
     vsa_hs_corpus *c = new (std::nothrow) vsa_hs_corpus;
@@ -798,8 +806,18 @@ int vsa_hs_corpus_prepare(const vsa_hs_database_t *db, vsa_hs_scratch_t *scratch
     return VSA_HS_SUCCESS;
 }
 
+int vsa_hs_corpus_prepare(const vsa_hs_database_t *db, vsa_hs_scratch_t *scratch,
+                          const uint8_t *d_data, const uint8_t *h_data,
+                          const uint64_t *offsets, const uint64_t *lens,
+                          const uint32_t *stream_ids, uint32_t nblocks,
+                          vsa_hs_corpus_t **out) {
+    return corpus_prepare(db, scratch, d_data, h_data, offsets, lens, stream_ids, nblocks, false,
+                          out);
+}
+
 int vsa_hs_corpus_free(vsa_hs_corpus_t *c) {
     if (!c) return VSA_HS_SUCCESS;
+    vsa_report::device_report_free(c->report);
     vsa_plan_free(c->plan);
     vsa_plan_free(c->plan2);
     if (c->ctx2) vsa_ctx_destroy(c->ctx2);
@@ -1176,6 +1194,8 @@ int vsa_hs_corpus_scan_ex(vsa_hs_corpus_t *cp, uint64_t *counts, uint64_t *diges
                           uint64_t *total, unsigned threads) {
     if (!cp || !total || !valid_db(cp->db)) return VSA_HS_INVALID;
     const vsa_hs_database *db = cp->db;
+    /* a device-prepared corpus has no host copy for the long-literal check */
+    if (cp->report && db->max_len > SHORT_LIT) return VSA_HS_INVALID;
     vsa_hs_scratch *scratch = cp->scratch;
     int rc = enter(db, scratch);
     if (rc != VSA_HS_SUCCESS) return rc;
@@ -1229,6 +1249,7 @@ int vsa_hs_corpus_scan_repeats(vsa_hs_corpus_t *cp, uint32_t repeats, uint64_t *
                                uint64_t *counts, uint64_t *digests, unsigned threads) {
     if (!cp || !totals || !repeats || !valid_db(cp->db)) return VSA_HS_INVALID;
     const vsa_hs_database *db = cp->db;
+    if (cp->report && db->max_len > SHORT_LIT) return VSA_HS_INVALID;
     if (db->simple && !counts && !digests) {
         /* one record = one match: the GPU's counts, nothing to replay */
         for (uint32_t k = 0; k < repeats; k++) {
@@ -1465,6 +1486,227 @@ int vsa_hs_report_records_host(const vsa_hs_database_t *db, const uint64_t *keys
         *total += em.cnt;
     }
     return VSA_HS_SUCCESS;
+}
+
+/* ------------------------------------------ the report program in passes --
+ * hs_report_passes.h: the same report program as data-parallel passes.  The
+ * device runs them in report.hip; vsa_hs_report_records_emulated runs the
+ * same bodies and the same run_passes in serial loops on the CPU. */
+extern "C++" {
+namespace {
+
+/* run_passes' backend on the CPU.  Every buffer is its own allocation of
+ * exactly the size asked for, so that an index past it is one a sanitizer
+ * sees. */
+struct HostBackend {
+    void *slot[vsa_report::S_COUNT] = {};
+    ~HostBackend() {
+        for (void *p : slot) free(p);
+    }
+    template <class T>
+    int buf(vsa_report::Slot s, uint64_t count, T **out) {
+        if (count > (1ULL << 60) / sizeof(T)) return VSA_E_NOMEM;
+        free(slot[s]);
+        slot[s] = malloc(count ? (size_t)(count * sizeof(T)) : 1);
+        if (!slot[s]) return VSA_E_NOMEM;
+        *out = (T *)slot[s];
+        return VSA_OK;
+    }
+    template <class F>
+    int each(uint64_t n, const F &f) {
+        if (n && !vsa_report::grid_for(n)) return VSA_E_INVALID;
+        for (uint64_t i = 0; i < n; i++) f(i);
+        return VSA_OK;
+    }
+    int exclusive_sum(const uint64_t *in, uint64_t *out, uint64_t n) {
+        std::exclusive_scan(in, in + n, out, (uint64_t)0);
+        return VSA_OK;
+    }
+    int sort_pairs(const uint64_t *kin, uint64_t *kout, const uint64_t *vin, uint64_t *vout,
+                   uint64_t n, int end_bit) {
+        const uint64_t mask = end_bit >= 64 ? ~0ULL : (1ULL << end_bit) - 1;
+        std::vector<uint64_t> idx(n);
+        std::iota(idx.begin(), idx.end(), (uint64_t)0);
+        std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+            return (kin[a] & mask) < (kin[b] & mask);
+        });
+        for (uint64_t i = 0; i < n; i++) {
+            kout[i] = kin[idx[i]];
+            vout[i] = vin[idx[i]];
+        }
+        return VSA_OK;
+    }
+    int read_u64(const uint64_t *src, uint64_t *dst) {
+        *dst = *src;
+        return VSA_OK;
+    }
+    void stage(vsa_report::Stage) {}
+};
+
+void fill_blocks(vsa_report::Blocks &b, const vsa_report::BlockTable &bt, const uint64_t *so,
+                 const uint64_t *se, const uint32_t *order, const uint64_t *offsets,
+                 const uint64_t *lens, uint32_t nblocks) {
+    b.so = so;
+    b.se = se;
+    b.order = order;
+    b.offsets = offsets;
+    b.lens = lens;
+    b.npos = (uint32_t)bt.so.size();
+    b.nblocks = nblocks;
+    b.uniform = bt.uniform;
+    b.off0 = bt.off0;
+    b.ulen = bt.ulen;
+}
+
+/* per block, the digest of its matches: m = all blocks' matches, blocks in
+ * index order */
+void fold_digests(const vsa_hs_match_t *m, const uint64_t *counts, uint32_t nblocks,
+                  uint64_t *digests) {
+    uint64_t at = 0;
+    for (uint32_t b = 0; b < nblocks; b++) {
+        uint64_t h = 0;
+        for (uint64_t k = 0; k < counts[b]; k++, at++)
+            h = vsa_hs_seq_digest_step(h, m[at].id, m[at].from, m[at].to);
+        digests[b] = h;
+    }
+}
+
+int hs_code(int vsa_rc) {
+    return vsa_rc == VSA_OK         ? VSA_HS_SUCCESS
+           : vsa_rc == VSA_E_NOMEM  ? VSA_HS_NOMEM
+           : vsa_rc == VSA_E_INVALID ? VSA_HS_INVALID
+                                     : VSA_HS_UNKNOWN_ERROR;
+}
+
+} // namespace
+} // extern "C++"
+
+int vsa_hs_report_records_emulated(const vsa_hs_database_t *db, const uint64_t *keys,
+                                   const uint32_t *ids, uint64_t n, const uint8_t *h_data,
+                                   const uint64_t *offsets, const uint64_t *lens,
+                                   uint32_t nblocks, uint64_t *counts, uint64_t *digests,
+                                   vsa_hs_match_t *out, uint64_t cap, uint64_t *total) {
+    if (!valid_db(db) || !total || (n && (!keys || !ids)) || (nblocks && (!offsets || !lens)))
+        return VSA_HS_INVALID;
+    if (db->mode != VSA_HS_MODE_BLOCK) return VSA_HS_DB_MODE_ERROR;
+    if (db->max_len > SHORT_LIT && !h_data && nblocks) return VSA_HS_INVALID;
+    for (uint64_t k = 0; k < n; k++)
+        if (ids[k] >= db->frags.size() || (k && keys[k] < keys[k - 1])) return VSA_HS_INVALID;
+    vsa_report::BlockTable bt;
+    if (!vsa_report::build_block_table(offsets, lens, nblocks, bt)) return VSA_HS_INVALID;
+    ReportTables r;
+    build_report_tables(db, r);
+    vsa_report::Pass p{};
+    p.t = r.t;
+    fill_blocks(p.b, bt, bt.so.data(), bt.se.data(), bt.order.data(), offsets, lens, nblocks);
+    p.data = h_data;
+    p.keys = keys;
+    p.ids = ids;
+    p.n = n;
+    HostBackend be;
+    *total = 0;
+    if (int rc = vsa_report::run_passes(be, p, total)) return hs_code(rc);
+    if (counts) std::copy(p.bcnt, p.bcnt + nblocks, counts);
+    if (digests) fold_digests(p.out, p.bcnt, nblocks, digests);
+    if (out) std::copy(p.out, p.out + std::min(cap, *total), out);
+    return VSA_HS_SUCCESS;
+}
+
+int vsa_hs_corpus_prepare_device(const vsa_hs_database_t *db, vsa_hs_scratch_t *scratch,
+                                 const uint8_t *d_data, const uint64_t *offsets,
+                                 const uint64_t *lens, uint32_t nblocks, vsa_hs_corpus_t **out) {
+    if (!valid_db(db) || !offsets || !lens || !out || (nblocks && !d_data))
+        return VSA_HS_INVALID;
+    if (db->mode != VSA_HS_MODE_BLOCK) return VSA_HS_DB_MODE_ERROR;
+    if (nblocks > VSA_MAX_BLOCKS) return VSA_HS_INVALID;
+    vsa_report::BlockTable bt;
+    if (!vsa_report::build_block_table(offsets, lens, nblocks, bt)) return VSA_HS_INVALID;
+    vsa_hs_corpus *c = nullptr;
+    int rc = corpus_prepare(db, scratch, d_data, nullptr, offsets, lens, nullptr, nblocks, true,
+                            &c);
+    if (rc != VSA_HS_SUCCESS) return rc;
+    vsa_report::DeviceTables *tabs = nullptr;
+    for (auto &e : scratch->rtabs)
+        if (e.first == db->serial) tabs = e.second;
+    if (!tabs) {
+        ReportTables r;
+        build_report_tables(db, r);
+        rc = hs_code(vsa_report::device_tables_create(scratch->ctx, r.t, r.pool.size(), &tabs));
+        if (rc != VSA_HS_SUCCESS) {
+            vsa_hs_corpus_free(c);
+            return rc;
+        }
+        scratch->rtabs.emplace_back(db->serial, tabs);
+    }
+    rc = hs_code(vsa_report::device_report_create(scratch->ctx, tabs, bt, offsets, lens, nblocks,
+                                                  d_data, &c->report));
+    if (rc != VSA_HS_SUCCESS) {
+        vsa_hs_corpus_free(c);
+        return rc;
+    }
+    *out = c;
+    return VSA_HS_SUCCESS;
+}
+
+/* the scan completed (overflow rescans and the fallback sort included), then
+ * the passes over its records; the caller holds the scratch */
+static int corpus_scan_device(vsa_hs_corpus *cp, uint64_t *counts, uint64_t *total) {
+    vsa_hs_scratch *scratch = cp->scratch;
+    vsa_db_t *ddb = device_db(scratch, cp->db);
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t nm = 0;
+    const uint64_t *d_keys = nullptr;
+    const uint32_t *d_ids = nullptr;
+    if (cp->plan &&
+        (vsa_scan_plan(scratch->ctx, ddb, cp->plan, 0, &nm) != VSA_OK ||
+         vsa_scan_wait(scratch->ctx, &nm) != VSA_OK ||
+         vsa_scan_results(scratch->ctx, &d_keys, &d_ids) != VSA_OK))
+        return VSA_HS_UNKNOWN_ERROR;
+    static const bool timing = getenv("VSA_HOST_TIMING") != nullptr;
+    if (timing)
+        fprintf(stderr, "vsa_hs_corpus_scan_device: scan %.3f ms (%llu records)\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                    .count(),
+                (unsigned long long)nm);
+    return hs_code(vsa_report::device_report_run(cp->report, d_keys, d_ids, nm, counts, total));
+}
+
+int vsa_hs_corpus_scan_device(vsa_hs_corpus_t *cp, uint64_t *counts, uint64_t *total) {
+    if (!cp || !total || !valid_db(cp->db) || !cp->report) return VSA_HS_INVALID;
+    int rc = enter(cp->db, cp->scratch);
+    if (rc != VSA_HS_SUCCESS) return rc;
+    *total = 0;
+    rc = corpus_scan_device(cp, counts, total);
+    leave(cp->scratch);
+    return rc;
+}
+
+int vsa_hs_corpus_matches_device(vsa_hs_corpus_t *cp, const vsa_hs_match_t **d_matches,
+                                 uint64_t *n) {
+    if (!cp || !cp->report || !d_matches || !n) return VSA_HS_INVALID;
+    return hs_code(vsa_report::device_report_matches(cp->report, d_matches, n));
+}
+
+int vsa_hs_corpus_scan_matches(vsa_hs_corpus_t *cp, vsa_hs_match_t *out, uint64_t cap,
+                               uint64_t *counts, uint64_t *digests, uint64_t *total) {
+    if (!cp || !total || !valid_db(cp->db) || !cp->report) return VSA_HS_INVALID;
+    int rc = enter(cp->db, cp->scratch);
+    if (rc != VSA_HS_SUCCESS) return rc;
+    *total = 0;
+    const uint32_t nblocks = (uint32_t)cp->offsets.size();
+    std::vector<uint64_t> own_counts;
+    if (digests && !counts) {
+        own_counts.assign(nblocks, 0);
+        counts = own_counts.data();
+    }
+    if (!out) cap = 0;
+    rc = corpus_scan_device(cp, counts, total);
+    if (rc == VSA_HS_SUCCESS && digests && cap < *total) rc = VSA_HS_INVALID;
+    if (rc == VSA_HS_SUCCESS)
+        rc = hs_code(vsa_report::device_report_copy(cp->report, out, std::min(cap, *total)));
+    if (rc == VSA_HS_SUCCESS && digests) fold_digests(out, counts, nblocks, digests);
+    leave(cp->scratch);
+    return rc;
 }
 
 /* runtime.c:545-575 */

@@ -30,6 +30,13 @@
 
 #include "../../include/vectorscan_amd_hs.h"
 
+/* the functions below also run as device code (report.hip) */
+#if defined(__HIP__)
+#define VSA_HD __host__ __device__
+#else
+#define VSA_HD
+#endif
+
 namespace vsa_report {
 
 constexpr uint32_t NO_EKEY = ~0u;
@@ -53,7 +60,7 @@ struct Tables {
 };
 
 /* first record of keys[0, n) whose key is >= key */
-inline uint64_t lower_bound_key(const uint64_t *keys, uint64_t n, uint64_t key) {
+VSA_HD inline uint64_t lower_bound_key(const uint64_t *keys, uint64_t n, uint64_t key) {
     uint64_t lo = 0, hi = n;
     while (lo < hi) {
         const uint64_t mid = lo + (hi - lo) / 2;
@@ -66,7 +73,7 @@ inline uint64_t lower_bound_key(const uint64_t *keys, uint64_t n, uint64_t key) 
 /* CHECK_LONG_LIT for a pattern ending at `to` of the block at blk: `to` is
  * tested against the length before any byte is loaded, and only bytes of
  * [blk, blk + to) are read */
-inline bool pat_live(const Tables &t, const Pat &p, const uint8_t *blk, uint64_t to) {
+VSA_HD inline bool pat_live(const Tables &t, const Pat &p, const uint8_t *blk, uint64_t to) {
     if (p.len <= SHORT_LEN) return true;
     if (to < p.len) return false;
     const uint8_t *s = blk + (to - p.len);
@@ -92,7 +99,7 @@ inline bool pat_live(const Tables &t, const Pat &p, const uint8_t *blk, uint64_t
  * id was reported before iff an earlier pattern of the group has that id,
  * reports directly (no SOM log) and passes its long-literal check. */
 template <class Ex, class Emit>
-inline void report_group(const Tables &t, const uint32_t *ids, uint64_t k0, uint64_t k1,
+VSA_HD inline void report_group(const Tables &t, const uint32_t *ids, uint64_t k0, uint64_t k1,
                          const uint8_t *blk, uint64_t to, Ex &ex, Emit &emit) {
     bool som_logged = false;
     for (uint64_t k = k0; k < k1; k++) {
@@ -134,7 +141,7 @@ inline void report_group(const Tables &t, const uint32_t *ids, uint64_t k0, uint
         uint64_t best = ~0ULL;
         uint32_t best_len = 0;
         for (uint64_t k = k0; k < k1; k++) {
-                const uint32_t f = ids[k];
+            const uint32_t f = ids[k];
             for (uint32_t pi = t.frag_off[f]; pi < t.frag_off[f + 1]; pi++) {
                 const Pat p = t.pats[pi];
                 if (!(p.flags & PAT_SOM_DEDUPE) || p.id < lo || p.id > best) continue;

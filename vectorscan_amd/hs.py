@@ -421,17 +421,20 @@ _sig("vsa_hs_corpus_scan_repeats", ctypes.c_int, _vp, ctypes.c_uint32, _vp, _vp,
 _sig("vsa_hs_corpus_free", ctypes.c_int, _vp)
 _sig("vsa_hs_report_records_host", ctypes.c_int, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,
      ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64, _u64p)
+_sig("vsa_hs_report_records_emulated", ctypes.c_int, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp,
+     _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64, _u64p)
+_sig("vsa_hs_corpus_prepare_device", ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32,
+     ctypes.POINTER(_vp))
+_sig("vsa_hs_corpus_scan_device", ctypes.c_int, _vp, _vp, _u64p)
+_sig("vsa_hs_corpus_matches_device", ctypes.c_int, _vp, ctypes.POINTER(_vp), _u64p)
+_sig("vsa_hs_corpus_scan_matches", ctypes.c_int, _vp, _vp, ctypes.c_uint64, _vp, _vp, _u64p)
 
 # vsa_hs_match_t
 MATCH_DTYPE = np.dtype([("id", np.uint32), ("block", np.uint32), ("from", np.uint64),
                         ("to", np.uint64)])
 
 
-def report_records_host(db, keys, ids, data, offsets, lens, cap=None):
-    """vsa_hs_report_records_host: the report program on the CPU over sorted
-    HWLM records (keys = end << 24 | order, ends relative to `data`), each
-    block one hs_scan.  Returns (rc, total, counts, digests, matches as a
-    MATCH_DTYPE array of at most cap entries; default: all)."""
+def _report_records(fn, db, keys, ids, data, offsets, lens, cap):
     keys = np.ascontiguousarray(keys, np.uint64)
     ids = np.ascontiguousarray(ids, np.uint32)
     offs = np.ascontiguousarray(offsets, np.uint64)
@@ -444,7 +447,7 @@ def report_records_host(db, keys, ids, data, offsets, lens, cap=None):
     total = ctypes.c_uint64()
 
     def call(out, c):
-        return lib.vsa_hs_report_records_host(
+        return fn(
             db.handle, keys.ctypes.data, ids.ctypes.data, len(keys), hp, offs.ctypes.data,
             ln.ctypes.data, n, cnt.ctypes.data, dg.ctypes.data,
             out.ctypes.data if out is not None else None, c, ctypes.byref(total))
@@ -456,6 +459,24 @@ def report_records_host(db, keys, ids, data, offsets, lens, cap=None):
     out = np.zeros(max(1, cap), MATCH_DTYPE)
     rc = call(out, cap)
     return rc, total.value, cnt, dg, out[:min(cap, total.value)]
+
+
+def report_records_host(db, keys, ids, data, offsets, lens, cap=None):
+    """vsa_hs_report_records_host: the report program on the CPU over sorted
+    HWLM records (keys = end << 24 | order, ends relative to `data`), each
+    block one hs_scan.  Returns (rc, total, counts, digests, matches as a
+    MATCH_DTYPE array of at most cap entries; default: all)."""
+    return _report_records(lib.vsa_hs_report_records_host, db, keys, ids, data, offsets, lens,
+                           cap)
+
+
+def report_records_emulated(db, keys, ids, data, offsets, lens, cap=None):
+    """vsa_hs_report_records_emulated: report_records_host computed by the
+    device path's passes (lead, exhaustion sort, count, sums, emit) in serial
+    loops on the CPU; same arguments and results.  Non-empty blocks that
+    overlap are refused (INVALID)."""
+    return _report_records(lib.vsa_hs_report_records_emulated, db, keys, ids, data, offsets,
+                           lens, cap)
 
 _M64 = (1 << 64) - 1
 
@@ -478,7 +499,8 @@ class Corpus:
     """vsa_hs_corpus_t: device-resident blocks prepared once (launch plan,
     stream grouping) for repeated vsa_hs_corpus_scan calls."""
 
-    def __init__(self, db, scratch, d_data, offsets, lens, stream_ids=None, h_data=None):
+    def __init__(self, db, scratch, d_data, offsets, lens, stream_ids=None, h_data=None,
+                 device_report=False):
         self._offs = np.ascontiguousarray(offsets, np.uint64)
         self._lens = np.ascontiguousarray(lens, np.uint64)
         self._sid = (np.ascontiguousarray(stream_ids, np.uint32)
@@ -488,10 +510,20 @@ class Corpus:
             self._hk, hp, _ = _as_buf(h_data)
         self.n = len(self._offs)
         h = _vp()
-        rc = lib.vsa_hs_corpus_prepare(db.handle, scratch.handle, d_data, hp,
-                                       self._offs.ctypes.data, self._lens.ctypes.data,
-                                       self._sid.ctypes.data if self._sid is not None else None,
-                                       self.n, ctypes.byref(h))
+        self.device_report = bool(device_report)
+        if device_report:
+            # the report program on the device: no host copy, block mode only
+            if stream_ids is not None or h_data is not None:
+                raise ValueError("device_report takes neither stream_ids nor h_data")
+            rc = lib.vsa_hs_corpus_prepare_device(db.handle, scratch.handle, d_data,
+                                                  self._offs.ctypes.data,
+                                                  self._lens.ctypes.data, self.n,
+                                                  ctypes.byref(h))
+        else:
+            rc = lib.vsa_hs_corpus_prepare(
+                db.handle, scratch.handle, d_data, hp, self._offs.ctypes.data,
+                self._lens.ctypes.data, self._sid.ctypes.data if self._sid is not None else None,
+                self.n, ctypes.byref(h))
         if rc:
             raise HsError(rc)
         self.handle = h.value
@@ -521,6 +553,44 @@ class Corpus:
                                             cnt.ctypes.data if cnt is not None else None,
                                             dg.ctypes.data if dg is not None else None, threads)
         return rc, tot, cnt, dg
+
+    def scan_device(self, counts=False):
+        """vsa_hs_corpus_scan_device (device_report corpora): scan and report
+        program on the device, the matches stay there (matches_device).
+        (rc, total, per-block counts or None)"""
+        cnt = np.zeros(self.n, np.uint64) if counts else None
+        total = ctypes.c_uint64()
+        rc = lib.vsa_hs_corpus_scan_device(self.handle,
+                                           cnt.ctypes.data if cnt is not None else None,
+                                           ctypes.byref(total))
+        return rc, total.value, cnt
+
+    def matches_device(self):
+        """vsa_hs_corpus_matches_device: (rc, device address of the last
+        scan_device's MATCH_DTYPE entries, their number)"""
+        p, n = _vp(), ctypes.c_uint64()
+        rc = lib.vsa_hs_corpus_matches_device(self.handle, ctypes.byref(p), ctypes.byref(n))
+        return rc, p.value, n.value
+
+    def scan_matches(self, cap=None, counts=False, digests=False):
+        """vsa_hs_corpus_scan_matches: scan_device plus the matches copied to
+        the host.  (rc, total, counts or None, digests or None, MATCH_DTYPE
+        array of min(cap, total) entries; cap None: all of them, taken from a
+        first scan's total)"""
+        cnt = np.zeros(self.n, np.uint64) if counts else None
+        dg = np.zeros(self.n, np.uint64) if digests else None
+        total = ctypes.c_uint64()
+        if cap is None:
+            rc = lib.vsa_hs_corpus_scan_device(self.handle, None, ctypes.byref(total))
+            if rc:
+                return rc, 0, cnt, dg, np.zeros(0, MATCH_DTYPE)
+            cap = total.value
+        out = np.zeros(max(1, cap), MATCH_DTYPE)
+        rc = lib.vsa_hs_corpus_scan_matches(self.handle, out.ctypes.data, cap,
+                                            cnt.ctypes.data if cnt is not None else None,
+                                            dg.ctypes.data if dg is not None else None,
+                                            ctypes.byref(total))
+        return rc, total.value, cnt, dg, out[:min(cap, total.value)]
 
     def close(self):
         if self.handle:

@@ -2,6 +2,7 @@
 
     python -m vectorscan_amd.hsbench -e EXPRS [-s SIGFILE | -z ID] -c CORPUS.db
         [-N | -V] [-n REPEATS] --literal-on [--per-scan] [--echo-matches] [--json]
+        [--device-report]
 
 Mirrors the reference's tools/hsbench (main.cpp): expressions are lines
 ``ID:/literal/flags`` (util/expressions.cpp:59-94 processLine,
@@ -23,6 +24,11 @@ on a CPU thread.  The timed region of a repeat is that call (launch, device
 sort, count / record replay, synchronisation); the report
 lines and calc_mbps (main.cpp:705-708: bytes / (seconds * 125000)) are the
 reference's, with "per core" meaning per GPU.
+
+--device-report (block mode only, off by default): the report program runs on
+the device too (vsa_hs_corpus_prepare_device / _scan_device), no host copy of
+the corpus is kept for it, and --echo-matches prints from the matches the
+device returns.
 """
 import argparse
 import json
@@ -183,8 +189,11 @@ def layout(blocks, mode):
 class GpuCorpus:
     """The corpus resident in HBM plus the compiled database and scratch."""
 
-    def __init__(self, exprs, ids, flags, blocks, mode):
+    def __init__(self, exprs, ids, flags, blocks, mode, device_report=False):
+        if device_report and mode != hs.MODE_BLOCK:
+            raise ValueError("device_report is for block mode")
         self.mode = mode
+        self.device_report = device_report
         full_mode = mode | (hs.MODE_SOM_HORIZON_LARGE if mode == hs.MODE_STREAM else 0)
         t0 = time.perf_counter()
         self.db = hs.compile_lit_multi(exprs, flags, ids, full_mode)
@@ -195,12 +204,19 @@ class GpuCorpus:
         self.d_data = self.ctx.malloc(max(1, self.image.nbytes))
         self.ctx.h2d(self.d_data, self.image)
         self.long = any(len(e) > 8 for e in exprs)
+        if device_report:
+            self.corpus = hs.Corpus(self.db, self.scratch, self.d_data, self.offs, self.lens,
+                                    device_report=True)
+            return
         self.corpus = hs.Corpus(self.db, self.scratch, self.d_data, self.offs, self.lens,
                                 self.sids if mode != hs.MODE_BLOCK else None,
                                 self.image if self.long else None)
 
     def scan(self, counts=False, threads=16):
-        rc, total, cnt = self.corpus.scan(counts, threads)
+        if self.device_report:
+            rc, total, cnt = self.corpus.scan_device(counts)
+        else:
+            rc, total, cnt = self.corpus.scan(counts, threads)
         if rc != hs.SUCCESS:
             raise hs.HsError(rc)
         return total, cnt
@@ -208,18 +224,32 @@ class GpuCorpus:
     def scan_digests(self, threads=16):
         """(total, per-block counts, per-block callback-sequence digests,
         hs.seq_digest) of one corpus scan"""
-        rc, total, cnt, dg = self.corpus.scan(True, threads, digests=True)
+        if self.device_report:
+            rc, total, cnt, dg, _ = self.corpus.scan_matches(counts=True, digests=True)
+        else:
+            rc, total, cnt, dg = self.corpus.scan(True, threads, digests=True)
         if rc != hs.SUCCESS:
             raise hs.HsError(rc)
         return total, cnt, dg
 
     def scan_repeats(self, repeats, threads=16):
         """per-pass totals of `repeats` pipelined passes (pass k + 1 on the
-        GPU while pass k replays on the host)"""
+        GPU while pass k replays on the host); with device_report the
+        passes run one after the other, nothing replays on the host"""
+        if self.device_report:
+            return [self.scan()[0] for _ in range(repeats)]
         rc, tot, _, _ = self.corpus.scan_repeats(repeats, False, threads)
         if rc != hs.SUCCESS:
             raise hs.HsError(rc)
         return [int(t) for t in tot]
+
+    def matches(self):
+        """device_report: one scan's matches, a hs.MATCH_DTYPE array (blocks
+        in scan order, each block's in delivery order)"""
+        rc, _, _, _, m = self.corpus.scan_matches()
+        if rc != hs.SUCCESS:
+            raise hs.HsError(rc)
+        return m
 
     def close(self):
         self.corpus.close()
@@ -265,6 +295,9 @@ def main(argv=None):
     ap.add_argument("--echo-matches", action="store_true")
     ap.add_argument("--json", action="store_true", help="also print a JSON summary line")
     ap.add_argument("--replay-threads", type=int, default=16)
+    ap.add_argument("--device-report", action="store_true",
+                    help="block mode: the report program on the device, no host copy of "
+                         "the corpus")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="one pass at a time (per-pass times); the default overlaps "
                          "pass k + 1's GPU scan with pass k's host replay")
@@ -276,6 +309,9 @@ def main(argv=None):
         print("Error: Couldn't parse argument to -n flag, should be a positive integer.")
         return 1
     mode = hs.MODE_BLOCK if a.block else (hs.MODE_VECTORED if a.vectored else hs.MODE_STREAM)
+    if a.device_report and mode != hs.MODE_BLOCK:
+        print("Error: --device-report needs block mode (-N)")
+        return 1
     expr_map = load_expressions(a.exprs)
     sig_ids = None
     sig_name = "all"
@@ -290,7 +326,7 @@ def main(argv=None):
         print("Corpus data error: %s" % e)
         return 1
     try:
-        g = GpuCorpus(exprs, ids, flags, blocks, mode)
+        g = GpuCorpus(exprs, ids, flags, blocks, mode, a.device_report)
     except hs.HsError as e:
         if e.expression >= 0:
             print("Compile error for signature #%d: %s" % (e.expression, e.message))
@@ -315,7 +351,7 @@ def main(argv=None):
         if i >= 7 and time.perf_counter() - t_w > 0.25:
             break
     secs, totals = [], []
-    pipelined = not (a.no_pipeline or a.per_scan)
+    pipelined = not (a.no_pipeline or a.per_scan or a.device_report)
     t_all = time.perf_counter()
     if pipelined:
         # passes overlap, so a pass has no time of its own: each is the mean
@@ -357,7 +393,8 @@ def main(argv=None):
                           "matches": totals[0], "repeats": a.repeats,
                           "mean_mbps": calc_mbps(total_secs, nbytes * a.repeats),
                           "max_mbps": calc_mbps(min(secs), nbytes),
-                          "best_ms": min(secs) * 1e3, "pipelined": pipelined}))
+                          "best_ms": min(secs) * 1e3, "pipelined": pipelined,
+                          "device_report": bool(a.device_report)}))
     g.close()
     return 0
 
@@ -366,6 +403,11 @@ def echo(g, blocks, mode):
     """--echo-matches (engine_hyperscan.cpp:103-115): every match through
     the callback API, per block (block mode) or per stream."""
     db, scratch = g.db, g.scratch
+    if g.device_report:  # block mode: the matches as the device returned them
+        m = g.matches()
+        for b, to, i in zip(m["block"].tolist(), m["to"].tolist(), m["id"].tolist()):
+            print("Match @%u:%u for %u" % (blocks[b][0], to, i))
+        return
     if mode == hs.MODE_BLOCK:
         for cid, _, data in blocks:
             _, seq = hs.scan(db, data, scratch)
